@@ -2,6 +2,7 @@
 """Headline benchmark: env-steps/s of wildfire_v0 random-policy rollouts on MI355X (BASELINE.json config 2).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+                    [--dump-outputs DIR]                   (what the last timed step computed, as DIR/<name>.npy: see dump_outputs)
 
 A "step" is one pass of the hot path over one batch: the fused HIP kernel samples the uniform random policy and performs one
 ParallelEnv.step() for all parallel_envs (action decode, 7 transitions, rewards / termination, open action / observation space
@@ -43,6 +44,7 @@ BATCH_PER_GPU = 65536  # BASELINE.json configs[1]
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 PROBE_EPISODES = 4     # whole episodes behind the kernel-level figures (independent of --steps)
 MIN_BLOCKS, TARGET_TIMED_S = 10, 0.05
+DUMP_BUDGET_BYTES, DUMP_SAMPLE_SEED = 64 << 20, 20260104  # --dump-outputs: at most 64 MB; beyond that a fixed, seeded sample of the envs
 
 
 def wildfire_bytes_per_env_step(HW, A, k, mean_tasks, mean_agent_tasks_sum, injected_randomness=False, state_passes=2.0):
@@ -272,7 +274,7 @@ def secondary_workloads(device, B):
 
 def mt19937_workload(device, B, K, base_seed, policy_seed, seed_stride, repeats, barrier):
     """The headline block in the DEFAULT rng mode of the drop-in env (rng='mt19937': per-env MT19937 streams in HBM, bit-identical to the
-    reference's CPU RandomGenerator for the same seeds, /root/reference utils/random_generator.py:49-146 — north_star's identical-seeds parity
+    reference's CPU RandomGenerator for the same seeds, the reference's utils/random_generator.py:49-146 — north_star's identical-seeds parity
     mode), N = 1 only, never part of `value`.  Same protocol as the headline: K-step blocks of <= 50-step episodes, reseed +
     reset + steps + metrics per episode, each block bracketed by barrier + synchronize, median block.  The block is ONE HIP graph here (the
     streams are re-seeded by a launch of their own, so an episode is not a single launch)."""
@@ -337,10 +339,63 @@ def mt19937_workload(device, B, K, base_seed, policy_seed, seed_stride, repeats,
     return out
 
 
+def _list_rows(values, offsets, counts, envs):
+    """The rows [offsets[b], offsets[b] + counts[b]) of a packed list for the envs ``envs``, concatenated in that order (the same rows
+    whether the library packs the lists or gives every env a fixed stride)."""
+    starts, n = offsets[envs], counts[envs]
+    return values[np.repeat(starts - np.cumsum(n) + n, n) + np.arange(int(n.sum()))]
+
+
+def dump_outputs(env, metrics, out_dir):
+    """What the last timed step left for a caller, as ``out_dir/<name>.npy``: the state (``env.state()``), rewards, flags, the sampled
+    actions, the observation records, the packed task / action-mapping lists and their counts, the episode metrics of the timed blocks.
+    Env-major ([B, ...]); floats as they are, integers as float64, flags as float32.  ``env_index`` names the envs written: all of them,
+    or a fixed, seeded sample where the whole batch would exceed DUMP_BUDGET_BYTES."""
+    state = env.state()
+    host = lambda t: t.detach().cpu().numpy()  # noqa: E731
+    A = len(env.agents)
+    dense = {'fires': host(state.fires), 'intensity': host(state.intensity), 'fuel': host(state.fuel), 'suppressants': host(state.suppressants),
+             'capacity': host(state.capacity), 'equipment': host(state.equipment), 'num_moves': host(env._num_moves),
+             'num_burnouts': host(env._num_burnouts), 'burnouts': host(env._burnouts), 'putouts': host(env._putouts),
+             'rewards': host(env._rewards.t()), 'cumulative_rewards': host(env._cumulative.t()), 'terminations': host(env._terminations.t()),
+             'truncations': host(env._truncations.t()), 'actions': host(env._actions.transpose(0, 1)), 'obs_self': host(env._obs_self.transpose(0, 1)),
+             'obs_others': host(env._obs_others.transpose(0, 1)), 'env_task_count': host(env._env_task_count),
+             'agent_task_count': host(env._agent_task_count.t())}
+    lists = [('tasks', host(env._task_values), host(env._task_offsets), dense['env_task_count']),
+             ('observation_mapping', host(env._obs_map_values), host(env._task_offsets), dense['env_task_count'])]
+    lists += [(f'action_mapping_{a}', host(env._act_map_values[a]), host(env._act_map_offsets[a]), dense['agent_task_count'][:, a]) for a in range(A)]
+    if env._bad_map_values is not None:
+        bad = dense['env_task_count'][:, None] - dense['agent_task_count']
+        lists += [(f'bad_actions_{a}', host(env._bad_map_values[a]), host(env._bad_map_offsets[a]), bad[:, a]) for a in range(A)]
+
+    def arrays(envs):
+        out = {name: value[envs] for name, value in dense.items()}
+        out.update((name, _list_rows(values, offsets, counts, envs)) for name, values, offsets, counts in lists)
+        out = {name: value if value.dtype in (np.float32, np.float64) else value.astype(np.float32 if value.dtype == np.bool_ else np.float64)
+               for name, value in out.items()}
+        out['env_index'] = envs.astype(np.float64)
+        out['metrics'] = host(metrics).astype(np.float64)
+        return out
+
+    B = env.parallel_envs
+    envs = np.arange(B)
+    out = arrays(envs)
+    size = sum(value.nbytes for value in out.values())
+    while size > DUMP_BUDGET_BYTES:
+        keep = max(1, int(len(envs) * 0.95 * DUMP_BUDGET_BYTES / size))
+        envs = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=keep, replace=False))
+        out = arrays(envs)
+        size = sum(value.nbytes for value in out.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, value in out.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), value)
+    return {'dir': out_dir, 'arrays': len(out), 'bytes': size, 'envs': len(envs), 'sampled': len(envs) < B}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=500)
+    ap.add_argument('--steps', type=int, default=500, help='steps of the timed rollout block (K): every timed block runs exactly K steps')
     ap.add_argument('--warmup', type=int, default=100)
     ap.add_argument('--rng', choices=['philox', 'mt19937'], default='philox')
     ap.add_argument('--batch', type=int, default=BATCH_PER_GPU, help='parallel_envs per GPU')
@@ -348,6 +403,8 @@ def main():
     ap.add_argument('--no-secondary', action='store_true', help='skip the cybersecurity / rideshare rollouts reported beside the headline')
     ap.add_argument('--no-episode-probe', action='store_true', help='skip the whole-episode (50-step) launches timed beside the block\'s own launch and the '
                     'auto-reset workload: a kernel trace of the run then shows the block\'s launch in a row of its own')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed blocks, write what the last timed step computed as DIR/<name>.npy '
+                    '(float32 / float64, at most 64 MB; rank 0\'s envs): the same arguments give the same inputs, so builds compare output for output')
     args = ap.parse_args()
     if args.steps <= 0:
         raise SystemExit('--steps must be positive')
@@ -456,6 +513,8 @@ def main():
         job_metrics.copy_(metrics)
         sharding.reduce_metrics(job_metrics)
     finished_metrics = (job_metrics if dist is not None else metrics).clone()
+    # the outputs of the timed path, before anything else runs on the env (the probes below step it again)
+    dumped = dump_outputs(env, finished_metrics, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # what a per-block reduction would have cost (never part of `value`): the same block with the all-reduce inside, same bracketing
     collective_probe_s = []
     if dist is not None:
@@ -839,6 +898,7 @@ def main():
             'auto_reset_workload': dense,
             'recorded_rollout_workload': recorded,
             'reference_cpu_env_steps_per_s': {'value': 21112, 'source': 'BASELINE.md §2: unmodified reference, 8 vCPU, B=65536 (survey container)'},
+            'dumped_outputs': dumped,
         }
         if world == 1 and not args.no_cpu_baseline:
             try:

@@ -1,10 +1,17 @@
 """ctypes binding of the C-ABI in include/frz.h to libfrz_hip.so (hand-written HIP kernels, gfx950).
 
 There is NO CPU fallback: if the shared library is missing or a symbol cannot be resolved, loading fails loudly.
+
+One HIP runtime per process: libfrz_hip.so needs ``libamdhip64.so.7`` and is handed torch's streams and allocations, so it must bind
+to the runtime torch ships.  torch is imported here, before anything can load the library: the library's dependency then resolves to
+torch's already-loaded runtime by soname.  Loaded first, it would pull in the system runtime, and torch would add its own beside it
+(torch asks for ``libamdhip64.so`` by its own rpath): two runtimes, each given the other's stream handles.
 """
 import ctypes
 import os
 from typing import Any, Dict
+
+import torch  # noqa: F401  (torch's HIP runtime first: see above)
 
 from ._cstruct import parse_header
 
@@ -114,6 +121,12 @@ class FrzError(RuntimeError):
     """A C-ABI entry point returned a negative FRZ_E_* code."""
 
 
+def hip_runtimes() -> set:
+    """The distinct HIP runtime files (libamdhip64) mapped into this process."""
+    with open('/proc/self/maps') as maps:
+        return {fields[5] for fields in (line.split() for line in maps) if len(fields) > 5 and 'libamdhip64' in os.path.basename(fields[5])}
+
+
 def lib() -> ctypes.CDLL:
     """Load libfrz_hip.so once; raise (never fall back) if it is not built."""
     global _lib
@@ -129,6 +142,10 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = argtypes
         if handle.frz_abi_version() != DEFINES['FRZ_ABI_VERSION']:
             raise ImportError('libfrz_hip.so ABI version does not match include/frz.h; rebuild')
+        runtimes = hip_runtimes()
+        if len(runtimes) > 1:
+            raise ImportError(f'{len(runtimes)} HIP runtimes are loaded in this process ({", ".join(sorted(runtimes))}): libfrz_hip.so '
+                              'must share torch\'s (import torch before anything loads a HIP runtime)')
         _lib = handle
     return _lib
 

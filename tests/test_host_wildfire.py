@@ -76,6 +76,21 @@ def test_header_symbols_are_bound_and_exported():
     assert handle.frz_abi_version() == _capi.DEFINES['FRZ_ABI_VERSION']
 
 
+def test_one_hip_runtime_whatever_loads_the_library_first():
+    """build()'s order in a fresh process — the package, libfrz_hip.so through ctypes, then torch (the op shim), then the bound library —
+    leaves ONE HIP runtime mapped: torch's, which the library shares (a second runtime would be handed the first one's streams)."""
+    if not os.path.exists(_capi.LIB_PATH):
+        pytest.skip('libfrz_hip.so not built')
+    import subprocess
+    import sys
+    script = ('import ctypes, json, sys; sys.path.insert(0, sys.argv[1]); from free_range_zoo_amd import _capi; ctypes.CDLL(_capi.LIB_PATH); '
+              'import torch; _capi.lib(); print(json.dumps(sorted(_capi.hip_runtimes())))')
+    done = subprocess.run([sys.executable, '-c', script, _capi.REPO_ROOT], capture_output=True, text=True, timeout=300)
+    assert done.returncode == 0, done.stderr[-2000:]
+    runtimes = json.loads(done.stdout.strip().splitlines()[-1])
+    assert len(runtimes) == 1, runtimes
+
+
 def test_create_argument_checks_and_arena_size():
     if not os.path.exists(_capi.LIB_PATH):
         pytest.skip('libfrz_hip.so not built')

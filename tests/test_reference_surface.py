@@ -1,47 +1,23 @@
-"""Drop-in surface check against the reference's SOURCE TEXT (no import): configuration dataclasses carry the same field names,
-the env base class takes the same constructor keywords, the baselines / wrappers packages export the same class names.
+"""Drop-in surface check against the reference's public surface: configuration dataclasses carry the same field names, the env base
+class takes the same constructor keywords, the baselines / wrappers packages export the same class names.
 
-Runs only where /root/reference exists (the build container); parses the files with ``ast`` — nothing of the reference is executed
-or copied.  Skipped elsewhere (the GPU box has no reference tree)."""
-import ast
+The reference's side is tests/golden/reference_surface.json: the names parsed (``ast``, nothing executed) from the reference's source
+text by tools/refharness/make_golden.py surface."""
 import importlib
 import inspect
+import json
 import os
 
 import pytest
 
-REF = '/root/reference/free_range_zoo'
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+with open(os.path.join(GOLDEN, 'reference_surface.json')) as _handle:
+    SURFACE = json.load(_handle)
 
 
-def _tree(relative):
-    with open(os.path.join(REF, relative)) as handle:
-        return ast.parse(handle.read())
-
-
-def _dataclass_fields(tree):
-    """{class name: [annotated field names]} for every class of a module (dataclass fields are the annotated assignments)."""
-    out = {}
-    for node in tree.body:
-        if isinstance(node, ast.ClassDef):
-            out[node.name] = [stmt.target.id for stmt in node.body if isinstance(stmt, ast.AnnAssign) and isinstance(stmt.target, ast.Name)]
-    return out
-
-
-def _function_args(tree, class_name, function_name):
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ClassDef) and node.name == class_name:
-            for stmt in node.body:
-                if isinstance(stmt, ast.FunctionDef) and stmt.name == function_name:
-                    names = [a.arg for a in stmt.args.args + stmt.args.kwonlyargs]
-                    return [n for n in names if n != 'self']
-    raise AssertionError(f'{class_name}.{function_name} not found')
-
-
-@needs_reference
 @pytest.mark.parametrize('domain', ['wildfire', 'rideshare', 'cybersecurity'])
 def test_configuration_dataclasses_have_the_reference_fields(domain):
-    reference = _dataclass_fields(_tree(f'envs/{domain}/env/structures/configuration.py'))
+    reference = SURFACE['configuration_fields'][domain]
     mine = importlib.import_module(f'free_range_zoo_amd.envs.{domain}.env.structures.configuration')
     checked = 0
     for name, fields in reference.items():
@@ -55,10 +31,9 @@ def test_configuration_dataclasses_have_the_reference_fields(domain):
     assert checked >= 4
 
 
-@needs_reference
 @pytest.mark.parametrize('domain', ['wildfire', 'rideshare', 'cybersecurity'])
 def test_state_dataclasses_have_the_reference_fields(domain):
-    reference = _dataclass_fields(_tree(f'envs/{domain}/env/structures/state.py'))
+    reference = SURFACE['state_fields'][domain]
     mine = importlib.import_module(f'free_range_zoo_amd.envs.{domain}.env.structures.state')
     for name, fields in reference.items():
         if name.endswith('State') and fields:
@@ -66,9 +41,8 @@ def test_state_dataclasses_have_the_reference_fields(domain):
             assert own == fields, f'{domain}.{name}: fields {own} != reference {fields}'
 
 
-@needs_reference
 def test_env_constructor_keywords_cover_the_reference():
-    reference = _function_args(_tree('utils/env.py'), 'BatchedAECEnv', '__init__')
+    reference = SURFACE['env_init_args']
     from free_range_zoo_amd.utils.env import BatchedAECEnv as BatchedEnv
     own = list(inspect.signature(BatchedEnv.__init__).parameters)
     for name in reference:
@@ -76,7 +50,7 @@ def test_env_constructor_keywords_cover_the_reference():
     for domain, extra in (('wildfire', ['observe_other_suppressant', 'observe_other_power', 'show_bad_actions']),
                           ('cybersecurity', ['observe_other_location', 'observe_other_presence', 'observe_other_power', 'partially_observable',
                                              'show_bad_actions'])):
-        args = _function_args(_tree(f'envs/{domain}/env/{domain}.py'), 'raw_env', '__init__')
+        args = SURFACE['raw_env_init_args'][domain]
         for name in extra:
             assert name in args, f'{domain}: the reference constructor no longer takes {name}?'
         module = importlib.import_module(f'free_range_zoo_amd.envs.{domain}.env.{domain}')
@@ -95,11 +69,9 @@ def test_env_methods_of_the_reference_exist():
         assert callable(module.parallel_env) and callable(module.env)
 
 
-@needs_reference
 @pytest.mark.parametrize('domain', ['wildfire', 'rideshare', 'cybersecurity'])
 def test_baseline_packages_export_the_reference_classes(domain):
-    tree = _tree(f'envs/{domain}/baselines/__init__.py')
-    names = [alias.asname or alias.name for node in tree.body if isinstance(node, ast.ImportFrom) for alias in node.names]
+    names = SURFACE['baseline_exports'][domain]
     mine = importlib.import_module(f'free_range_zoo_amd.envs.{domain}.baselines')
     assert names, domain
     for name in names:
@@ -108,17 +80,16 @@ def test_baseline_packages_export_the_reference_classes(domain):
         assert callable(getattr(cls, 'act', None)) and callable(getattr(cls, 'observe', None))
 
 
-@needs_reference
 def test_random_generator_and_agent_interfaces():
-    reference = _tree('utils/random_generator.py')
+    reference = SURFACE['random_generator_args']
     from free_range_zoo_amd.utils.random_generator import RandomGenerator
     for method in ('seed', 'generate'):
-        args = _function_args(reference, 'RandomGenerator', method)
+        args = reference[method]
         own = list(inspect.signature(getattr(RandomGenerator, method)).parameters)
         for name in args:
             assert name in own, f'RandomGenerator.{method}({name}) missing'
-    assert _function_args(reference, 'RandomGenerator', '__init__') == [p for p in inspect.signature(RandomGenerator.__init__).parameters if p != 'self']
-    agent = _function_args(_tree('utils/agent.py'), 'Agent', '__init__')
+    assert reference['__init__'] == [p for p in inspect.signature(RandomGenerator.__init__).parameters if p != 'self']
+    agent = SURFACE['agent_init_args']
     from free_range_zoo_amd.utils.agent import Agent
     assert agent == [p for p in inspect.signature(Agent.__init__).parameters if p != 'self']
 
@@ -129,8 +100,6 @@ def test_random_generator_and_agent_interfaces():
 import pickle  # noqa: E402
 
 import torch  # noqa: E402
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def _same(a, b, path=''):

@@ -14,9 +14,13 @@ Parts:
   spaces    the objects raw_env.action_space(agent) / observation_space(agent) of the reference hand out at the reset and after every
             step of the recorded trajectories (the same runs, replayed from the same seeds), as structure: kind, n, start, low, high,
             members — what the reference's builders (envs/*/env/spaces/*.py) pass to free_range_rust's constructors.
+  surface   the reference's public surface as names (read with ``ast``, nothing executed): dataclass fields of the configuration and
+            state modules, constructor keywords of the env classes, the classes the baselines packages export, the parameters of
+            RandomGenerator and Agent (tests/test_reference_surface.py).
 
 Fixtures hold DATA only (inputs / expected outputs / the plain-C configuration fields), never reference source.
 """
+import ast
 import inspect
 import json
 import os
@@ -1265,7 +1269,54 @@ def record_spaces():
         run('rideshare', name, env, steps, rideshare_policy, np.random.default_rng(seed), lambda aec: aec.environment_task_count)
 
 
-PARTS = {'spaces': record_spaces, 'partial': record_partial_resets, 'rng': record_rng, 'ka': record_known_answers, 'baselines_wildfire': record_wildfire_baselines, 'baselines_rideshare': record_rideshare_baselines, 'baselines_cybersecurity': record_cyber_baselines, 'logs': record_logs, 'logs_sql': record_sql_logs, 'pickles': record_pickles, 'traj_wildfire': record_wildfire_trajectories, 'traj_cybersecurity': record_cyber_trajectories,
+# ----------------------------------------------------------------------------------------------------------
+# the reference's public surface, as names parsed from its source text (tests/test_reference_surface.py)
+# ----------------------------------------------------------------------------------------------------------
+def _reference_tree(relative):
+    with open(os.path.join(shim.REFERENCE_ROOT, 'free_range_zoo', relative)) as handle:
+        return ast.parse(handle.read())
+
+
+def _dataclass_fields(tree):
+    """{class name: [annotated field names]} for every class of a module (dataclass fields are the annotated assignments)."""
+    out = {}
+    for node in tree.body:
+        if isinstance(node, ast.ClassDef):
+            out[node.name] = [stmt.target.id for stmt in node.body if isinstance(stmt, ast.AnnAssign) and isinstance(stmt.target, ast.Name)]
+    return out
+
+
+def _function_args(tree, class_name, function_name):
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ClassDef) and node.name == class_name:
+            for stmt in node.body:
+                if isinstance(stmt, ast.FunctionDef) and stmt.name == function_name:
+                    names = [a.arg for a in stmt.args.args + stmt.args.kwonlyargs]
+                    return [n for n in names if n != 'self']
+    raise AssertionError(f'{class_name}.{function_name} not found')
+
+
+def record_surface():
+    domains = ('wildfire', 'rideshare', 'cybersecurity')
+    generator = _reference_tree('utils/random_generator.py')
+    out = {
+        'configuration_fields': {d: _dataclass_fields(_reference_tree(f'envs/{d}/env/structures/configuration.py')) for d in domains},
+        'state_fields': {d: _dataclass_fields(_reference_tree(f'envs/{d}/env/structures/state.py')) for d in domains},
+        'env_init_args': _function_args(_reference_tree('utils/env.py'), 'BatchedAECEnv', '__init__'),
+        'raw_env_init_args': {d: _function_args(_reference_tree(f'envs/{d}/env/{d}.py'), 'raw_env', '__init__') for d in ('wildfire', 'cybersecurity')},
+        'baseline_exports': {d: [alias.asname or alias.name for node in _reference_tree(f'envs/{d}/baselines/__init__.py').body
+                                 if isinstance(node, ast.ImportFrom) for alias in node.names] for d in domains},
+        'random_generator_args': {m: _function_args(generator, 'RandomGenerator', m) for m in ('__init__', 'seed', 'generate')},
+        'agent_init_args': _function_args(_reference_tree('utils/agent.py'), 'Agent', '__init__'),
+    }
+    path = os.path.join(GOLDEN, 'reference_surface.json')
+    with open(path, 'w') as handle:
+        json.dump(out, handle, indent=1, sort_keys=True)
+        handle.write('\n')
+    print(path, os.path.getsize(path), 'bytes')
+
+
+PARTS = {'spaces': record_spaces, 'surface': record_surface, 'partial': record_partial_resets, 'rng': record_rng, 'ka': record_known_answers, 'baselines_wildfire': record_wildfire_baselines, 'baselines_rideshare': record_rideshare_baselines, 'baselines_cybersecurity': record_cyber_baselines, 'logs': record_logs, 'logs_sql': record_sql_logs, 'pickles': record_pickles, 'traj_wildfire': record_wildfire_trajectories, 'traj_cybersecurity': record_cyber_trajectories,
          'traj_rideshare': record_rideshare_trajectories,
          'misc': record_misc}
 
